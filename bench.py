@@ -15,6 +15,21 @@ One step = one pass of the hot path over the rank's shard, inputs resident in HB
 No host synchronisation inside the step.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--global-batch G] [--config B|C|L]
+                  [--dump-outputs DIR] [--full]
+
+A plain run does what `value` needs and no more: set up, W warm-up steps, the K timed steps, the
+result line (metric, value, unit, ms_per_step, the workload, the selected candidate, the solved
+fraction).  `--full` adds every other measurement to the same line, after (per-config: before)
+the timed steps: the per-config lines, the event and per-kernel timing passes and the kernel's
+solver-flops count with the roofline built from them, the PCIe-inclusive, generated-input and
+per-tick host lines, the CPU baseline, and at N > 1 the serial-selection and weak-scaling
+lines; the `--no-*` options trim a `--full` run.
+
+`--dump-outputs DIR` writes what the last timed step left in the caller's arrays, copied right
+after the timed region: DIR/U.npy [B, nu N], cost.npy, status.npy, iters.npy [B] and
+selected.npy ([global index, cost, U...] decoded from the selection record), float64 (at N > 1
+each rank writes its shard as <name>_rank<r>.npy).  Above 64 MB in all, a seeded sample of the
+rows is written and rows.npy names them.  The inputs are a function of the arguments alone.
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment launches N ranks itself
 (`python -m torch.distributed.run --nproc-per-node N ...` as a child process; this parent makes
@@ -490,6 +505,28 @@ def synthetic_shard(B, nV, seed, rank, index_base):
     return cost, status, U
 
 
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(path, arrays, selected, suffix=""):
+    """--dump-outputs: the per-instance outputs (each [B, ...]) and the decoded selection as
+    float64 .npy files; a seeded sample of the rows (rows.npy) where they exceed the limit."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    sel = np.asarray(selected, dtype=np.float64)
+    if arrays:
+        B = len(next(iter(arrays.values())))
+        row_bytes = sum(a[:1].nbytes for a in arrays.values()) + 8
+        keep = (DUMP_LIMIT_BYTES - sel.nbytes - 4096) // row_bytes
+        if B > keep:
+            rows = np.sort(np.random.default_rng(64).choice(B, size=keep, replace=False))
+            arrays = {k: a[rows] for k, a in arrays.items()}
+            arrays["rows"] = rows.astype(np.float64)
+    arrays["selected"] = sel
+    for k, a in arrays.items():
+        np.save(os.path.join(path, f"{k}{suffix}.npy"), np.ascontiguousarray(a))
+
+
 def main():
     argv = sys.argv[1:]
     ap = argparse.ArgumentParser()
@@ -502,6 +539,12 @@ def main():
                     help="instances per GPU of the weak-scaling (config D) line; 0 = skip")
     ap.add_argument("--config", default="B")
     ap.add_argument("--seed", type=int, default=20250404)
+    ap.add_argument("--full", action="store_true",
+                    help="every measurement beside the headline: per-config lines, kernel timing "
+                         "passes and the roofline, host-path lines, CPU baseline, and at N > 1 the "
+                         "serial-selection and weak-scaling lines (the --no-* options trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float64)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-per-config", action="store_true")
     ap.add_argument("--no-host-path", action="store_true",
@@ -520,6 +563,8 @@ def main():
                     help="N > 1: wait for each step's all-gather before the next solve (default: "
                          "the collective of step s overlaps the solve of step s + 1)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     fused = args.select == "fused"
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -579,9 +624,11 @@ def main():
             dist.broadcast_object_list(uid, src=0)
         group = Group(p, rank=(local, world, rank, uid[0]))
 
-    def run_line(batch_local, index_base, steps, warmup, serial=False):
+    def run_line(batch_local, index_base, steps, warmup, serial=False, detail=False, dump=False):
         """time `steps` steps of solve + selection on this rank's shard; returns
-        (elapsed max over ranks, kernel ms, select ms, best record, status, iters, eng).
+        (elapsed max over ranks, kernel ms, select ms, best record, status, iters, eng,
+        per-kernel times, the output arrays of the last timed step if dump).  detail: the event
+        and per-kernel timing passes and the solver-flops count after the timed steps (--full).
         N > 1: one all-gather of the ranks' records per step (mpcqp.dist.PipelinedSelect: step
         s's collective in flight while step s + 1 solves, unless serial; all of them complete
         inside the timed region)."""
@@ -661,9 +708,21 @@ def main():
             t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             elapsed = float(t.item())
+        # what the last timed step left: the selection record, and for --dump-outputs the
+        # per-instance arrays (the passes below run the same step again)
+        best_host = best.cpu().numpy()
+        outs = None
+        if dump:
+            outs = dict(U=U, cost=cost, status=status) if dry else \
+                {k: d[k].cpu().numpy() for k in ("U", "cost", "status", "iters")}
         mpc_ms = sel_ms = None
         kern = {}
-        if group is not None:
+        if dry:
+            status, iters = batch_local["status"], np.zeros(Bl, np.int32)
+        elif not detail:
+            status = d["status"].cpu().numpy()
+            iters = d["iters"].cpu().numpy()
+        elif group is not None:
             # the library's events around each solve call (slot 1) and kernel (2: the one-wave
             # kernel, 3: the overflow launch), a pass of `steps` more steps after the timed ones
             eng.enable_timing(True)
@@ -681,7 +740,7 @@ def main():
             kern["_solver_flops"] = count_solver_flops(eng, step, sync)
             status = d["status"].cpu().numpy()
             iters = d["iters"].cpu().numpy()
-        elif not dry:
+        else:
             # solve and selection durations: torch events around the calls, a separate pass of
             # `steps` more steps after the timed ones
             stream = torch.cuda.current_stream()
@@ -719,9 +778,7 @@ def main():
                 kern["_solver_flops"] = count_solver_flops(eng, step, sync)
             status = d["status"].cpu().numpy()
             iters = d["iters"].cpu().numpy()
-        else:
-            status, iters = batch_local["status"], np.zeros(Bl, np.int32)
-        return elapsed, mpc_ms, sel_ms, best.cpu().numpy(), status, iters, eng, kern
+        return elapsed, mpc_ms, sel_ms, best_host, status, iters, eng, kern, outs
 
     # ---- strong scaling: the global batch split over the ranks (the metric) ----------------
     if dry:
@@ -735,7 +792,7 @@ def main():
     # GPU work run while the clocks ramp (the headline kernel's first ~60 launches fall from
     # ~400 to ~355 us), and a short warm-up W would otherwise time them
     per = None
-    if world == 1 and not dry and not args.no_per_config:
+    if args.full and world == 1 and not dry and not args.no_per_config:
         per = {}
         for name, conf, Bc, gait in (("B@4096", "B", 4096, None),
                                      ("C@65536", "C", 65536, None),
@@ -747,13 +804,17 @@ def main():
                 per[name] = time_config(conf, Bc, args.seed, gait=gait)
             except Exception as exc:  # report, never hide
                 per[name] = dict(error=f"{type(exc).__name__}: {exc}")
-    elapsed, mpc_ms, sel_ms, best, status, iters, eng, kern = run_line(
-        local_batch, i0, args.steps, args.warmup, serial=args.serial_select)
+    elapsed, mpc_ms, sel_ms, best, status, iters, eng, kern, outs = run_line(
+        local_batch, i0, args.steps, args.warmup, serial=args.serial_select, detail=args.full,
+        dump=args.dump_outputs is not None)
     bcost, bidx, bU = decode_record(best)
+    if args.dump_outputs is not None:
+        dump_outputs(args.dump_outputs, outs, np.concatenate(([bidx, bcost], bU)),
+                     suffix="" if world == 1 else f"_rank{rank}")
     # N > 1: the same steps with each all-gather waited for before the next solve (reported
     # beside the overlapped value, never as it)
     serial_ms = None
-    if world > 1 and not args.serial_select and group is None:
+    if args.full and world > 1 and not args.serial_select and group is None:
         el_s, *rest = run_line(local_batch, i0, args.steps, args.warmup, serial=True)
         if rest[5] is not None:
             rest[5].close()
@@ -761,11 +822,11 @@ def main():
 
     # ---- weak scaling (config D at N = 8): 65,536 per GPU, independent shards -------------
     weak = None
-    if args.weak_batch and world > 1 and not dry:
+    if args.full and args.weak_batch and world > 1 and not dry:
         Bw = args.weak_batch
         wb = mpcqp.make_batch(p, Bw, seed=args.seed + 1000 + rank)
-        el_w, ms_w, _, best_w, st_w, _, eng_w, _ = run_line(wb, rank * Bw, args.steps,
-                                                            args.warmup)
+        el_w, ms_w, _, best_w, st_w, _, eng_w, _, _ = run_line(wb, rank * Bw, args.steps,
+                                                               args.warmup, detail=True)
         eng_w.close()
         cw, iw, _ = decode_record(best_w)
         weak = dict(batch_per_gpu=Bw, global_batch=Bw * world, value=Bw * world /
@@ -813,6 +874,14 @@ def main():
     if rank == 0 and dry:
         cfg["dry_run"] = "selection only: synthetic costs, gloo, no solve"
         out["config"] = cfg
+        print(json.dumps(out), flush=True)
+    elif rank == 0 and not args.full:
+        # the plain line: what the timed steps themselves give
+        cfg.update(solved_frac=solved, mean_solver_iters=float(iters.mean()),
+                   max_solver_iters=int(iters.max()), fast_path=eng.fast_path,
+                   select=args.select, kernel=eng.fused_kernel, lib_build_id=lib_build_id())
+        out["config"] = cfg
+        eng.close()
         print(json.dumps(out), flush=True)
     elif rank == 0:
         f_qp = flops_per_qp(p, iters.mean())

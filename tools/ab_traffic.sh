@@ -5,7 +5,7 @@
 set -o pipefail
 export TMPDIR=/tmp
 R=$(pwd)
-ARGS=${BENCH_ARGS:-"--steps 5 --warmup 1 --no-cpu-baseline --no-per-config"}
+ARGS=${BENCH_ARGS:-"--full --steps 5 --warmup 1 --no-cpu-baseline --no-per-config"}
 for n in "$@"; do
   if [ "$n" = default ]; then L=$R/mpc-limx-control_amd/lib/libmpcqp.so; else L=$R/mpc-limx-control_amd/lib/libmpcqp_$n.so; fi
   for c in FETCH_SIZE WRITE_SIZE; do

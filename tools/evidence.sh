@@ -21,11 +21,11 @@ run() {  # name timeout cmd...
   local n=$1 t=$2; shift 2
   timeout -k 10 $t "$@" > $O/$n.log 2>&1 || { echo "$n failed"; tail -n 5 $O/$n.log; exit 1; }
 }
-run bench 500 python3 bench.py
+run bench 500 python3 bench.py --full
 grep '^{' $O/bench.log > $O/bench.json
 # headline passes: a long warm-up so that the traced launches run at steady clocks, and no
 # host-path lines (they launch the same kernel and grid between PCIe copies)
-HB="--steps 20 --warmup ${HB_WARMUP:-100} --no-cpu-baseline --no-per-config --no-host-path"
+HB="--full --steps 20 --warmup ${HB_WARMUP:-100} --no-cpu-baseline --no-per-config --no-host-path"
 run B_trace 300 rocprofv3 --kernel-trace --stats -d $R/$O/B/trace -o run --output-format csv -- python3 bench.py $HB
 run B_fetch 200 rocprofv3 --pmc FETCH_SIZE -d $R/$O/B/fetch -o run --output-format csv -- python3 bench.py $HB
 run B_write 200 rocprofv3 --pmc WRITE_SIZE -d $R/$O/B/write -o run --output-format csv -- python3 bench.py $HB

@@ -6,7 +6,7 @@
 set -e
 OUT=${1:-gpurun_out/pmcf}
 shift || true
-if [ "$1" = "--driver" ]; then DRV=$2; ARGS=""; else DRV=bench.py; ARGS=${*:-"--steps 5 --warmup 1 --no-cpu-baseline --no-per-config"}; fi
+if [ "$1" = "--driver" ]; then DRV=$2; ARGS=""; else DRV=bench.py; ARGS=${*:-"--full --steps 5 --warmup 1 --no-cpu-baseline --no-per-config"}; fi
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 R=$(pwd)

@@ -7,7 +7,7 @@ set -o pipefail
 OUT=${1:-gpurun_out/stall}
 shift || true
 if [ "$1" = "--driver" ]; then DRV=$2; ARGS=""; else
-  DRV=bench.py; ARGS=${ARGS:-"--steps 20 --warmup 20 --no-cpu-baseline --no-per-config --no-host-path"}; fi
+  DRV=bench.py; ARGS=${ARGS:-"--full --steps 20 --warmup 20 --no-cpu-baseline --no-per-config --no-host-path"}; fi
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 R=$(pwd)

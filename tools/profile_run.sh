@@ -6,9 +6,9 @@
 # Counters are never combined with trace domains (pool rule).  Usage: tools/profile_run.sh OUT
 set -e
 OUT=${1:-gpurun_out/prof}
-ARGS=${BENCH_ARGS:-"--steps 10 --warmup 2 --no-cpu-baseline"}
+ARGS=${BENCH_ARGS:-"--full --steps 10 --warmup 2 --no-cpu-baseline"}
 # counter passes: the headline launches only (per_config's B-standing runs the same kernel)
-PMC_ARGS=${PMC_ARGS:-"--steps 10 --warmup 2 --no-cpu-baseline --no-per-config"}
+PMC_ARGS=${PMC_ARGS:-"--full --steps 10 --warmup 2 --no-cpu-baseline --no-per-config"}
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 R=$(pwd)

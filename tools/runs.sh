@@ -15,6 +15,8 @@
 set -o pipefail
 NAME=${1:?usage: tools/runs.sh <name> [tag]}
 T=${2:-$NAME}
+OUT=${RUNS_OUT:-runs_out}  # the full bench line of `bench` lands here
+mkdir -p "$OUT"
 mkdir -p gpurun_out
 
 rep() { local n=$1; shift; for r in $(seq "$n"); do "$@" || return 1; done; }
@@ -43,13 +45,13 @@ case "$NAME" in
   suite)      # the GPU suite (tools/gpu_tests.sh)
     TAG=$T bash tools/gpu_tests.sh ;;
   bench)      # the bench line driver-style (20 / 5) and steady state (200 / 100)
-    timeout -k 10 300 python3 bench.py --steps 200 --warmup 100 --no-per-config --no-host-path \
+    timeout -k 10 300 python3 bench.py --full --steps 200 --warmup 100 --no-per-config --no-host-path \
       > gpurun_out/${T}_long.json 2> gpurun_out/${T}_long.err &&
-    timeout -k 10 500 python3 bench.py > gpurun_out/${T}_drv.json 2> gpurun_out/${T}_drv.err ;;
+    timeout -k 10 500 python3 bench.py --full > "$OUT/${T}_drv.json" 2> "$OUT/${T}_drv.err" ;;
   shards)     # DESIGN §5's shard table and the bench step at --global-batch 8,192 / 4,096
     { timeout -k 10 300 python3 tools/shard_sweep.py --sizes 2048,4096,6144,8192,12288,65536 --reps 50 &&
       for g in 8192 4096; do
-        timeout -k 10 300 python3 bench.py --global-batch $g --no-per-config --no-host-path \
+        timeout -k 10 300 python3 bench.py --full --global-batch $g --no-per-config --no-host-path \
           --no-cpu-baseline > gpurun_out/${T}_b$g.json || exit 1
       done; } > gpurun_out/${T}.txt 2>&1 ;;
   smalltrace) # kernel trace of the shard sweep: the GPU's own durations at small shards
