@@ -427,6 +427,32 @@ double mpcqp_kernel_ms_sum(mpcqp_ctx *ctx, int which, int *count);
  * then resets it.  Other kernels add nothing. */
 int mpcqp_count_solver_flops(mpcqp_ctx *ctx, int on);
 double mpcqp_solver_flops(mpcqp_ctx *ctx, int *launches);
+/* (the count stays the algorithmic one over every instance of the call: an instance covered by
+ * its leader, below, counts its leader's solve) */
+
+/* Duplicate QPs in the two-QPs-per-wave kernel (explicit SRBM inputs).  Per aligned group of 16
+ * instances, the leader of an instance is the lowest-index instance of the group with the same
+ * contact word; an instance is covered when its leader is another instance and its x0, xref and
+ * lin equal the leader's bit for bit (as 64-bit integers: -0.0 differs from +0.0).  A covered
+ * instance is the same QP as its leader: it is not solved, and the leader's wavefront writes its
+ * U / cost / status / iterations rows too.  The kernel finds this from the inputs on every call;
+ * nothing is kept across calls.  Instances with more free variables than the kernel holds (the
+ * overflow launch's) are never covered.  MPCQP_PAIR_DEDUP=0 in the environment at context
+ * creation turns it off (every instance solved by itself); mpcqp_ctx_pair_dedup reports it.
+ * Diagnostic counter, as the solver-flops one: with on = 1 every paired-kernel launch adds the
+ * number of instances it covered; mpcqp_covered waits for the stream, returns the sum since the
+ * previous call (-1 if never enabled; *launches: the launches counted) and resets it. */
+/* mpcqp_ctx_pair_dedup: 1 only on a context whose paired kernel is built to look for duplicates
+ * (SRBM, explicit inputs) and with the switch on; the literal model's paired kernel never covers
+ * and reports 0.  The leader is found by the contact word's low 32 bits (every schedule bit at
+ * N <= 16) and the whole 64-bit word must then be equal: with bits set above 2N an instance may
+ * stay uncovered (and solve itself), never the reverse.
+ * mpcqp_ctx_pair_w4_min: the instances per launch from which the paired kernel runs at its
+ * 4-wave register budget (MPCQP_PAIR_W4_MIN at context creation; 0: never, or no paired kernel). */
+int mpcqp_ctx_pair_dedup(const mpcqp_ctx *ctx);
+int mpcqp_ctx_pair_w4_min(const mpcqp_ctx *ctx);
+int mpcqp_count_covered(mpcqp_ctx *ctx, int on);
+long long mpcqp_covered(mpcqp_ctx *ctx, int *launches);
 
 /* Diagnostics: per-phase cycle totals (s_memtime) of the fused kernels since the last call,
  * recorded only by the diagnostic build lib/libmpcqp_stamps.so (first call arms it); the

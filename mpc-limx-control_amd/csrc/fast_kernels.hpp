@@ -29,6 +29,8 @@ struct FastKernels {
     // the same at a 4-wave register budget, used from pair_w4_min instances per launch
     const void *pair_w4 = nullptr, *pair_gen_w4 = nullptr;
     int pair_w4_min = 0;
+    int pair_can_dedup = 0;  // the paired kernel is built to look for duplicate QPs of a group of 16
+    int pair_dedup = 0;      // ... and does (pair_can_dedup, unless MPCQP_PAIR_DEDUP=0)
     size_t pair_lds = 0;
     const void *wg = nullptr;  // workgroup per QP for the overflow list (nf <= 6N)
     size_t wg_lds = 0;

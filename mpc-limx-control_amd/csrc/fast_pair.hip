@@ -29,6 +29,12 @@ void add_pair(FastKernels &k) {
         k.pair_gen_w4 = (const void *)&k_mpc_pair<NU, N, MODEL, true, 4>;
     }
     k.pair_lds = PairLayout<NU, N, MODEL>::lds_bytes;
+    // the explicit-input kernel looks for duplicate QPs (pair_mpc's kDedup)
+#ifdef MPCQP_INPUT_ALIAS
+    k.pair_can_dedup = 0;
+#else
+    k.pair_can_dedup = (MPCQP_PAIR_SORT && MODEL == 0 && 2 * N <= 32) ? 1 : 0;
+#endif
     k.crash_k = MPCQP_PAIR_CRASH ? kPairCrashK : 0;
     k.crash_p = MPCQP_PAIR_CRASH ? kPairCrashP : 0;
 }

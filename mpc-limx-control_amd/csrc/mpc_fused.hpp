@@ -61,6 +61,13 @@ struct MpcArgs {
     // crash working-set solves and dual passes here (one atomic per wavefront, into slot
     // blockIdx % kFlopsSlots: 32,768 atomics on one address serialise); nullptr: off
     double *flops_acc;
+    // paired kernel, explicit SRBM inputs: an instance whose inputs equal, bit for bit, those of
+    // an earlier instance of its aligned group of 16 is not solved; the earlier one's wavefront
+    // writes its outputs too (mpc_pair.hpp; MPCQP_PAIR_DEDUP=0 at context creation: 0)
+    int dedup;
+    // diagnostic (mpcqp_count_covered): instances covered that way per launch, one atomic per
+    // wavefront that covers any, slotted as flops_acc; nullptr: off
+    unsigned long long *cov_acc;
     int cut;  // diagnostic cuts build only
     // device-generated inputs (GEN kernels): instance b = state b / cands,
     // candidate b % cands

@@ -106,6 +106,8 @@ constexpr int pair_pf() {
 #endif
 
 constexpr int kPairNF = 30;  // free variables per instance; lane 31 of a half carries g
+template <int V>
+struct PairInt { static constexpr int value = V; };  // a compile-time count passed to a lambda
 
 // a code-motion fence inside an unrolled dot product over an LDS buffer, with the four partial
 // sums pinned in registers: the compiler can neither hoist the later loads above it nor sink the
@@ -160,7 +162,8 @@ struct PairLayout {
     // (+ 2: the dual loop's zero slot and the crash's objective slot)
     static constexpr int eLate = oRow + 4 * NP + (MPCQP_PAIR_RINV ? 2 : NP + 2);
     static constexpr int nDoubles = ((eMid > eLate ? eMid : eLate) + 1) & ~1;
-    static constexpr size_t oCt = sizeof(double) * nDoubles;  // u64 contact mask, int64 index
+    // u64 contact mask; u64 [index (low word, -1: none) | mask of the covered instances]
+    static constexpr size_t oCt = sizeof(double) * nDoubles;
     static constexpr size_t oFid = oCt + 16;                  // int8 [NF]: variable of slot p
     static constexpr size_t oPos = oFid + NF;                 // int8 [NV]: slot of variable v
     static constexpr size_t bytes = (oPos + NV + 15) & ~(size_t)15;
@@ -201,7 +204,8 @@ __device__ __forceinline__ uint64_t gait_mask_half(int N, double Ts, double phas
 // schedule (the generated-input path: by gait phase within the cycle, which orders the
 // schedules), ties by index; wave w of the group gets ranks 2w' and 2w'+1.  Candidates of
 // one state with the same schedule are the same QP, so they land in the same wave.  Every
-// instance is still solved and written at its own index; only the pairing changes.
+// instance is written at its own index; only the pairing changes (and, with explicit inputs,
+// which of a group's identical QPs is solved: see below).
 // lane j of this lane's 16-lane row (DPP row_newbcast; j constant after unrolling)
 __device__ __forceinline__ int row_bcast_u32(int v, int j) {
     switch (j) {
@@ -213,23 +217,74 @@ __device__ __forceinline__ int row_bcast_u32(int v, int j) {
         default: return 0;
     }
 }
+// Explicit inputs: the candidates of one state that share a schedule are the same QP when their
+// x0 / xref / lin are equal too, and then only the first of them (the LEADER of its contact
+// word: the lowest index of the group with that word) needs a solve (see pair_mpc).  So the
+// leaders rank first, in word order, and share wavefronts; the others follow in (word, index)
+// order, and a wavefront whose two instances are both covered by their leaders leaves early.
+// A group of 16 distinct words ranks as by (word, index) alone.  `same`: the group's instances
+// with this half's word (bit j: instance g0 + j), its own bit included; 0 where the ranking
+// does not look for leaders.  (The ranking takes the word's low 32 bits, which hold every
+// schedule bit; the comparison in pair_mpc requires the whole 64-bit word to be equal, so with
+// bits set above 2N an instance may go uncovered that the definition by the full word covers:
+// conservative, never a different result.)
+// `cand`: those of `same` that can be this half's duplicates at all -- the lanes load one word
+// of each instance's x0 (the position's x, a continuous quantity) beside its contact word, in
+// the same round trip, and only instances whose word equals this half's go on to the full
+// comparison.  A group of distinct states thus pays one load and a few instructions.
 template <bool GEN, int N>
-__device__ __forceinline__ int pair_sorted_instance(const MpcArgs &a) {
+__device__ __forceinline__ int pair_sorted_instance(const MpcArgs &a, unsigned &same,
+                                                    unsigned &cand) {
     const int ln = lane(), c = ln & 15;
-    const int wv = xcd_order((int)blockIdx.x, (int)gridDim.x);
-    const int g0 = (2 * wv) & ~15;
+    int g0, wq;  // the group's first instance; this wavefront takes its ranks 2 wq and 2 wq + 1
+    if constexpr (!GEN && 2 * N <= 32) {
+        // The leaders' wavefronts are the ones that solve when the rest of their groups is
+        // covered.  Were they every eighth workgroup, they would trickle onto the chip behind
+        // seven wavefronts each that only compare and leave, and the dispatcher's round robin
+        // would keep putting them on the same few SIMDs.  So the launch runs pass-major: the
+        // first wavefront of every whole group (its leaders), then every group's second, and
+        // so on; the wavefronts of a short last group come at the end.  With a multiple of 8
+        // whole groups every wavefront of group g still runs on XCD g mod 8 (the dispatcher
+        // deals workgroups round robin over the XCDs), which keeps the group's rows in one L2.
+        const int w = (int)blockIdx.x, ngf = a.B >> 4;
+        if (w < 8 * ngf) {
+            wq = w / ngf;
+            g0 = 16 * (w - wq * ngf);
+        } else {
+            wq = w - 8 * ngf;
+            g0 = 16 * ngf;
+        }
+    } else {
+        const int wv = xcd_order((int)blockIdx.x, (int)gridDim.x);
+        g0 = (2 * wv) & ~15;
+        wq = wv & 7;
+    }
     const int gn = a.B - g0 < 16 ? a.B - g0 : 16;
     int rank = 0;
+    [[maybe_unused]] unsigned eq = 0, xw = 0;
     if constexpr (!GEN && 2 * N <= 32) {
-        // the schedule's bits (2k + foot, k < N) fit 32 bits: one DPP move and one compare per
+        // the schedule's bits (2k + foot, k < N) fit 32 bits: one DPP move and two compares per
         // candidate (bits above 2N, if a caller sets any, only change the pairing, never a result)
         unsigned key = ~0u;
         if (c < gn) key = (unsigned)a.contact[g0 + c];
+        if (a.dedup && c < gn) {  // x0[3] of instance g0 + c (x0 rows are 13 wide), folded to 32 bits
+            const long long xb = __double_as_longlong(a.x0[(size_t)(g0 + c) * 13 + 3]);
+            xw = (unsigned)xb ^ (unsigned)(xb >> 32);
+        }
+        unsigned lt = 0;
 #pragma unroll
         for (int j = 0; j < 16; ++j) {  // row_newbcast: key j of this 16-lane row
             const unsigned kj = (unsigned)row_bcast_u32((int)key, j);
-            rank += (j < gn && (kj < key || (kj == key && j < c))) ? 1 : 0;
+            lt |= (j < gn && kj < key) ? (1u << j) : 0u;
+            eq |= (j < gn && kj == key) ? (1u << j) : 0u;
         }
+        // sort key (not the first of its word, word, index): the leaders are the lanes with no
+        // equal word below them (every 16-lane row holds the same 16 keys: row 0 votes)
+        const unsigned below = (1u << c) - 1u;
+        const bool first = (eq & below) == 0u;
+        const unsigned lead = (unsigned)(__ballot(ln < 16 && c < gn && first) & 0xffffull);
+        rank = first ? __popc(lead & lt)
+                     : __popc(lead) + __popc(lt & ~lead) + __popc(eq & below) - 1;
     } else {
         unsigned long long key = ~0ull;
         if (c < gn) {
@@ -250,10 +305,24 @@ __device__ __forceinline__ int pair_sorted_instance(const MpcArgs &a) {
         }
     }
     // ranks 2w' (lower half) and 2w'+1 (upper half), both read off lanes 0-15 (row 0)
-    const int r0 = (2 * wv) & 15;
+    const int r0 = 2 * wq;
     const unsigned m0 = (unsigned)(__ballot(ln < 16 && c < gn && rank == r0) & 0xffffull);
     const unsigned m1 = (unsigned)(__ballot(ln < 16 && c < gn && rank == r0 + 1) & 0xffffull);
     const unsigned m = ln >= kHalf ? m1 : m0;
+    same = cand = 0;
+    if constexpr (!GEN && 2 * N <= 32) {
+        const int c0 = m0 ? __builtin_ctz(m0) : 0, c1 = m1 ? __builtin_ctz(m1) : 0;
+        const unsigned e0 = m0 ? (unsigned)__builtin_amdgcn_readlane((int)eq, c0) : 0u;
+        const unsigned e1 = m1 ? (unsigned)__builtin_amdgcn_readlane((int)eq, c1) : 0u;
+        same = ln >= kHalf ? e1 : e0;
+        if (a.dedup) {  // the instances whose x0 word equals this half's (row 0 votes)
+            const unsigned x0w = (unsigned)__builtin_amdgcn_readlane((int)xw, c0);
+            const unsigned x1w = (unsigned)__builtin_amdgcn_readlane((int)xw, c1);
+            const unsigned p0 = (unsigned)(__ballot(ln < 16 && xw == x0w) & 0xffffull);
+            const unsigned p1 = (unsigned)(__ballot(ln < 16 && xw == x1w) & 0xffffull);
+            cand = ln >= kHalf ? e1 & p1 : e0 & p0;
+        }
+    }
     return m ? g0 + __builtin_ctz(m) : a.B;  // a.B: no instance (rank beyond a short group)
 }
 
@@ -354,12 +423,22 @@ __device__ __forceinline__ void pair_mpc(const MpcArgs &a, unsigned char *smem) 
     using Lay = PairLayout<NU, N, MODEL>;
     using Sup = XSupport<MODEL>;
     constexpr int NX = 13, NS = NX + NU, NF = kPairNF, NV = Lay::NV, SD = Lay::SD, NP = kHalf;
+    // duplicate QPs of a group are solved once (the input phase, below): explicit SRBM inputs
+#ifdef MPCQP_INPUT_ALIAS
+    constexpr bool kDedup = false;
+#else
+    constexpr bool kDedup = MPCQP_PAIR_SORT && MODEL == 0 && !GEN && 2 * N <= 32;
+#endif
     MPCQP_STAMP_INIT(tst);
     const int ln = lane(), hl = ln & (kHalf - 1);
     const bool up = ln >= kHalf;
     int bq = 2 * xcd_order((int)blockIdx.x, (int)gridDim.x) + (up ? 1 : 0);
-    if constexpr (MPCQP_PAIR_SORT && MODEL == 0) bq = pair_sorted_instance<GEN, N>(a);
-    const bool valid = bq < a.B;
+    // the group's instances with this half's contact word, and those of them that may be its
+    // duplicates (explicit inputs)
+    unsigned same = 0, cand = 0;
+    if constexpr (MPCQP_PAIR_SORT && MODEL == 0) bq = pair_sorted_instance<GEN, N>(a, same, cand);
+    bool valid = bq < a.B;  // (a half covered by its leader, below, turns into a spare half)
+    unsigned cov = 0;       // the group's instances this half covers (bit j: instance g0 + j)
     const int b = valid ? bq : a.B - 1;  // the spare half of an odd batch re-reads the last QP
     [[maybe_unused]] const int b_ = b;
     unsigned char *Dbase = smem + (up ? Lay::bytes : 0);
@@ -415,6 +494,92 @@ __device__ __forceinline__ void pair_mpc(const MpcArgs &a, unsigned char *smem) 
         for (int r = 0; r < RX; ++r) v[r] = (hl + r * kHalf < NXR) ? stream_load(xrg + hl + r * kHalf) : 0.0;
         const double x0l = (hl < NX) ? stream_load(a.x0 + (size_t)b * NX + hl) : 0.0;
         if (MODEL == 0) contact = stream_load(a.contact + b);
+        if constexpr (kDedup) {
+            // ---- duplicate QPs.  The LEADER of an instance is the first instance of its group
+            //      of 16 with the same contact word (pair_sorted_instance).  An instance is
+            //      COVERED when its leader is another instance and its x0, xref and lin equal the
+            //      leader's bit for bit: then it is the same QP, and only the leader is solved.
+            //      A follower compares itself with its leader; a leader compares each later
+            //      instance of its word with itself -- the same test on the same data, so both
+            //      reach the same verdict with no flag in memory and no order between waves.
+            //      A covered follower turns into a spare half (no solve, no outputs, no selection
+            //      key); its leader writes its rows after its own (the outputs, below).
+            //      Instances that may go to the overflow kernel (more than NF free variables:
+            //      three per foot in contact at the most) are never covered, so whoever is
+            //      covered has a leader that is solved and written here.
+            //      Only the candidates the ranking left (`cand`: the same word of x0) are compared:
+            //      per candidate one word per lane of x0 / lin / contact (x0 on lanes 0-12, lin on
+            //      13-20, the contact word on 21) and its xref row, CH candidates per round trip
+            //      (the 3-wave build, which runs the small launches where a leader's wavefront is
+            //      the launch's critical path, takes a typical leader's seven at once).  Addresses
+            //      do not wait for this half's own loads.
+            constexpr uint64_t kSched = (1ull << (2 * N)) - 1ull;
+            typedef unsigned long long u64;
+            const int ci = bq & 15, g0 = bq & ~15;
+            const bool leads = (same & ((1u << ci) - 1u)) == 0u;
+            // whom to compare with: the later instances of the word, or the leader (lowest bit)
+            const unsigned rem = !(a.dedup && valid) ? 0u
+                                 : leads ? cand & ~((2u << ci) - 1u) : cand & same & (0u - same);
+            if (__ballot(rem != 0u) != 0ull) {
+                // (ordinary loads: a leader's rows are read by every one of its followers)
+                // (the lane's word of instance t sits at base + t * stride: one multiply-add each)
+                const u64 *base_a = hl < NX       ? reinterpret_cast<const u64 *>(a.x0 + hl)
+                                    : hl < NX + 8 ? reinterpret_cast<const u64 *>(a.lin + (hl - NX))
+                                                  : reinterpret_cast<const u64 *>(a.contact);
+                const unsigned stride_a = hl < NX ? NX : hl < NX + 8 ? 8 : 1;
+                auto word_a = [&](int t) -> u64 { return base_a[(size_t)(unsigned)t * stride_a]; };
+                auto xref_diff = [&](int t) -> u64 {
+                    const double *xt = a.xref + (size_t)t * NXR;
+                    u64 d = 0ull;
+#pragma unroll
+                    for (int r = 0; r < RX; ++r)
+                        if (hl + r * kHalf < NXR)
+                            d |= (u64)(__double_as_longlong(xt[hl + r * kHalf]) ^ __double_as_longlong(v[r]));
+                    return d;
+                };
+                constexpr int CH = W >= 4 ? 4 : 7;
+                const u64 own = word_a(b);
+                unsigned todo = rem;
+                // one round trip: the next NC candidates of each half, every load issued before
+                // the first is used (straight-line code; a spare slot re-reads the half's own row)
+                auto trip = [&](auto nc) {
+                    constexpr int NC = decltype(nc)::value;
+                    unsigned bit[NC];
+                    u64 d[NC];
+#pragma unroll
+                    for (int c = 0; c < NC; ++c) {
+                        bit[c] = todo & (0u - todo);
+                        todo &= ~bit[c];
+                        const int t = bit[c] ? g0 + __builtin_ctz(bit[c]) : b;
+                        d[c] = (word_a(t) ^ own) | xref_diff(t);
+                    }
+#pragma unroll
+                    for (int c = 0; c < NC; ++c)
+                        if (half_ballot(d[c] != 0ull) == 0u) cov |= bit[c];
+                };
+                do {  // (a wavefront of followers has one candidate per half: the narrow form)
+                    const unsigned tw = (unsigned)__builtin_amdgcn_readlane((int)todo, 0),
+                                   tu = (unsigned)__builtin_amdgcn_readlane((int)todo, kHalf);
+                    if (((tw & (tw - 1u)) | (tu & (tu - 1u))) == 0u) trip(PairInt<1>{});
+                    else trip(PairInt<CH>{});
+                } while (__ballot(todo != 0u) != 0ull);
+                // (instances that may overflow the kernel's capacity are not covered)
+                if (3 * __popcll(contact & kSched) > NF) cov = 0u;
+            }
+            if (!leads && cov) {  // covered by its leader
+                valid = false;
+                cov = 0u;
+            }
+            // a wavefront with nothing left to solve or write (both halves covered, or one
+            // covered and one past the batch) is done; in a fused selection it still takes its
+            // ticket, with no key
+            if (__ballot(valid) == 0ull) {
+                if (a.sel)
+                    sel_commit_t(a, kSelNone, NV, false,
+                                 reinterpret_cast<unsigned long long *>(smem) + Lay::oR, -1, ln);
+                return;
+            }
+        }
 #pragma unroll
         for (int r = 0; r < RX; ++r)
             if (hl + r * kHalf < NXR) xr[hl + r * kHalf] = v[r];
@@ -448,7 +613,9 @@ __device__ __forceinline__ void pair_mpc(const MpcArgs &a, unsigned char *smem) 
     uint64_t *ctl = reinterpret_cast<uint64_t *>(Dbase + Lay::oCt);
     if (hl == 0) {  // reloaded for the outputs: nothing per instance stays live
         ctl[0] = contact;
-        ctl[1] = (uint64_t)(valid ? bq : -1);
+        // (low word: the index, -1 for none; high word: the covered instances' mask, which
+        //  must not hold a register across the solve)
+        ctl[1] = (uint64_t)(unsigned)(valid ? bq : -1) | ((uint64_t)cov << 32);
     }
     wave_sync();
     // a wavefront whose two instances both go elsewhere (deferred to the workgroup kernel,
@@ -1659,11 +1826,34 @@ __device__ __forceinline__ void pair_mpc(const MpcArgs &a, unsigned char *smem) 
             stream_store(a.status + bo, status);
             stream_store(a.iters + bo, iters);
         }
+        // the instances this half covers (the input phase's verdict, parked beside the index)
+        // are the same QP: the same staged row, cost, status and iterations, at their rows
+        for (unsigned cm = kDedup ? (unsigned)(ctlo[1] >> 32) : 0u; cm != 0u; cm &= cm - 1u) {
+            const int bm = (bo & ~15) + __builtin_ctz(cm);
+            double *Um = a.U + (size_t)bm * NV;
+            for (int v = hlo; v < NV; v += kHalf) stream_store(Um + v, Us[v]);
+            if (hlo == 0) {
+                stream_store(a.cost + bm, fval);
+                stream_store(a.status + bm, status);
+                stream_store(a.iters + bm, iters);
+            }
+        }
     }
+    // (covered instances per half; a half without an instance or deferred covers none)
+    const int ncov = kDedup ? __popc((unsigned)(ctlo[1] >> 32)) : 0;
     if (a.flops_acc) {  // (diagnostic) both halves' solver flops, one atomic per wavefront
-        const double t = (double)__builtin_amdgcn_readlane(sfl, 0) +
-                         (double)__builtin_amdgcn_readlane(sfl, kHalf);
+        // the algorithmic count over every instance of the call: a covered instance's solve is
+        // its leader's
+        const double t =
+            (double)__builtin_amdgcn_readlane(sfl, 0) * (double)(1 + __builtin_amdgcn_readlane(ncov, 0)) +
+            (double)__builtin_amdgcn_readlane(sfl, kHalf) *
+                (double)(1 + __builtin_amdgcn_readlane(ncov, kHalf));
         if (lno == 0) atomicAdd(a.flops_acc + (blockIdx.x % kFlopsSlots) * kFlopsStride, t);
+    }
+    if (kDedup && a.cov_acc) {  // (diagnostic) covered instances, one atomic per wavefront that covers any
+        const int n = __builtin_amdgcn_readlane(ncov, 0) + __builtin_amdgcn_readlane(ncov, kHalf);
+        if (lno == 0 && n > 0)
+            atomicAdd(a.cov_acc + (blockIdx.x % kFlopsSlots) * kFlopsStride, (unsigned long long)n);
     }
 #ifndef MPCQP_FUSED_SEL
 #define MPCQP_FUSED_SEL 1

@@ -449,6 +449,12 @@ bool pick_fast(int model, int nx, int nu, int N, bool fric, int nfmax, FastKerne
     // working sets (0: the plain dual loop from the unconstrained minimum; A/B runs and tests)
     if (k.pair && k.crash_k > 0)
         if (const char *e = getenv("MPCQP_CRASH_P")) k.crash_p = std::max(0, atoi(e));
+    // MPCQP_PAIR_DEDUP=0: the paired kernel solves every instance itself, duplicates of a group
+    // included (mpc_pair.hpp; A/B runs and tests)
+    if (k.pair) {
+        const char *e = getenv("MPCQP_PAIR_DEDUP");
+        k.pair_dedup = k.pair_can_dedup && !(e && e[0] == '0');
+    }
     // the 4-wave build from this many instances per launch (MPCQP_PAIR_W4_MIN=n: A/B and tests;
     // 0 = never)
     if (k.pair) {
@@ -556,6 +562,9 @@ struct mpcqp_ctx {
     double *dflops = nullptr;  // diagnostic solver-flops accumulator (mpcqp_count_solver_flops)
     bool flops_on = false;
     int flops_launches = 0;
+    unsigned long long *dcov = nullptr;  // diagnostic covered-instance counter (mpcqp_count_covered)
+    bool cov_on = false;
+    int cov_launches = 0;
     unsigned long long *dsel = nullptr;     // k_select_min: per-block partial keys + ticket
     int *dlist = nullptr;                   // two overflow lists [count, -, ids...] (mpc_wg.hpp)
     size_t list_cap = 0;                    // instances a list holds
@@ -1059,6 +1068,47 @@ double mpcqp_solver_flops(mpcqp_ctx *c, int *launches) {
     return v;
 }
 
+int mpcqp_ctx_pair_dedup(const mpcqp_ctx *c) {
+    return c && c->fast && c->fk.pair && !c->fk.dense ? c->fk.pair_dedup : 0;
+}
+
+int mpcqp_ctx_pair_w4_min(const mpcqp_ctx *c) {
+    if (!c || !c->fast || !c->fk.pair || c->fk.dense || !c->fk.pair_w4) return 0;
+    return c->fk.pair_w4_min;
+}
+
+int mpcqp_count_covered(mpcqp_ctx *c, int on) {
+    if (!c) return MPCQP_ERR_BAD_ARG;
+    if (on && !c->dcov) {
+        hipSetDevice(c->device);
+        // (cleared on the context's stream: a later launch on it is ordered after the clear)
+        if (hipMalloc(&c->dcov, sizeof(unsigned long long) * kFlopsWords) != hipSuccess ||
+            hipMemsetAsync(c->dcov, 0, sizeof(unsigned long long) * kFlopsWords, c->stream) != hipSuccess) {
+            hipFree(c->dcov);
+            c->dcov = nullptr;
+            return MPCQP_ERR_DEVICE;
+        }
+    }
+    c->cov_on = on != 0;
+    return MPCQP_OK;
+}
+
+long long mpcqp_covered(mpcqp_ctx *c, int *launches) {
+    if (launches) *launches = 0;
+    if (!c || !c->dcov) return -1;
+    unsigned long long h[kFlopsWords], v = 0;
+    hipSetDevice(c->device);
+    // read and cleared on the context's stream, as mpcqp_solver_flops
+    if (hipMemcpyAsync(h, c->dcov, sizeof h, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+        hipMemsetAsync(c->dcov, 0, sizeof h, c->stream) != hipSuccess ||
+        hipStreamSynchronize(c->stream) != hipSuccess)
+        return -1;
+    for (int i = 0; i < kFlopsSlots; ++i) v += h[i * kFlopsStride];
+    if (launches) *launches = c->cov_launches;
+    c->cov_launches = 0;
+    return (long long)v;
+}
+
 int mpcqp_debug_phase_cycles(mpcqp_ctx *c, uint64_t *out, int n) {
 #ifdef MPCQP_STAMPS
     if (!c || !out || n <= 0) return MPCQP_ERR_BAD_ARG;
@@ -1097,6 +1147,7 @@ int mpcqp_ctx_destroy(mpcqp_ctx *c) {
     hipFree(c->dAB);
     hipFree(c->dstamps);
     hipFree(c->dflops);
+    hipFree(c->dcov);
     hipFree(c->dsel);
     hipFree(c->dlist);
     hipFree(c->hbuf);
@@ -1274,6 +1325,8 @@ static MpcArgs mpc_args(mpcqp_ctx *c, int B) {
     }
     a.stamps = c->dstamps;
     a.flops_acc = c->flops_on ? c->dflops : nullptr;
+    a.dedup = c->fk.pair_dedup;
+    a.cov_acc = c->cov_on ? c->dcov : nullptr;
     a.cut = 0;
 #ifdef MPCQP_CUTS
     if (const char *e = getenv("MPCQP_CUT")) a.cut = atoi(e);
@@ -1373,6 +1426,7 @@ static int launch_mpc(mpcqp_ctx *c, bool gen, int B, MpcArgs *a, bool may_overfl
     }
     a->sel_final = a->ovf ? 0 : 1;  // fused selection: the batch's last launch finalizes
     if (a->flops_acc && pk) ++c->flops_launches;
+    if (a->cov_acc && pk) ++c->cov_launches;
     tbegin(c, 2);
     int rc = pk ? launch(pk, (B + 1) / 2, c->fk.pair_lds, c->stream, a)
                 : launch(gen ? c->fk.mpc_gen : c->fk.mpc, B, c->fk.mpc_lds, c->stream, a);

@@ -27,6 +27,7 @@ EXPORTS = [
     "mpcqp_ctx_fast_path", "mpcqp_ctx_one_wave_nf", "mpcqp_ctx_overflow_kernel", "mpcqp_ctx_crash_params", "mpcqp_batch_discretize", "mpcqp_batch_condense_solve",
     "mpcqp_debug_phase_cycles", "mpcqp_batch_solve_host",
     "mpcqp_count_solver_flops", "mpcqp_solver_flops",
+    "mpcqp_ctx_pair_dedup", "mpcqp_ctx_pair_w4_min", "mpcqp_count_covered", "mpcqp_covered",
     "mpcqp_batch_select_min", "mpcqp_batch_select_record", "mpcqp_reduce_records",
     "mpcqp_batch_solve_select",
     "mpcqp_enable_timing", "mpcqp_last_kernel_ms", "mpcqp_kernel_ms_sum",
@@ -94,6 +95,12 @@ def lib():
         L.mpcqp_count_solver_flops.argtypes = [vp, i]
         L.mpcqp_solver_flops.argtypes = [vp, C.POINTER(C.c_int)]
         L.mpcqp_solver_flops.restype = C.c_double
+    if hasattr(L, "mpcqp_count_covered"):  # absent from A/B builds of older sources
+        L.mpcqp_ctx_pair_dedup.argtypes = [vp]
+        L.mpcqp_ctx_pair_w4_min.argtypes = [vp]
+        L.mpcqp_count_covered.argtypes = [vp, i]
+        L.mpcqp_covered.argtypes = [vp, C.POINTER(C.c_int)]
+        L.mpcqp_covered.restype = C.c_longlong
     L.mpcqp_batch_solve_host.argtypes = [vp, i] + [vp] * 8
     L.mpcqp_batch_discretize.argtypes = [vp, i, vp, vp]
     L.mpcqp_batch_condense_solve.argtypes = [vp, i] + [vp] * 8

@@ -259,6 +259,28 @@ class BatchEngine:
         v = float(lib().mpcqp_solver_flops(self.ctx, C.byref(n)))
         return v, n.value
 
+    @property
+    def pair_dedup(self) -> bool:
+        """k_mpc_pair solves each distinct QP of a group of 16 once (MPCQP_PAIR_DEDUP=0 at
+        context creation: off)"""
+        return bool(lib().mpcqp_ctx_pair_dedup(self.ctx))
+
+    @property
+    def pair_w4_min(self) -> int:
+        """instances per launch from which k_mpc_pair runs its 4-wave build (0: never)"""
+        return int(lib().mpcqp_ctx_pair_w4_min(self.ctx))
+
+    def count_covered(self, on=True):
+        """(diagnostic) k_mpc_pair counts the instances it covers (not solved: written by the
+        wavefront of the group's first instance with the same inputs)"""
+        check("mpcqp_count_covered", lib().mpcqp_count_covered(self.ctx, 1 if on else 0))
+
+    def covered(self):
+        """(instances covered since the previous call, paired-kernel launches counted); waits"""
+        n = C.c_int(0)
+        v = int(lib().mpcqp_covered(self.ctx, C.byref(n)))
+        return v, n.value
+
     def last_kernel_ms(self, which: int) -> float:
         """which: 0 stage 1, 1 the whole solve, 2 the one-wave fused kernel, 3 the overflow
         workgroup kernel (mpcqp.h)"""

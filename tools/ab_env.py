@@ -17,6 +17,8 @@ ap.add_argument("--env", action="append", required=True)
 ap.add_argument("--config", default="B")
 ap.add_argument("--gait", default="alternating")
 ap.add_argument("--batches", default="512,4096,8192,65536")
+ap.add_argument("--candidates", type=int, default=16,
+                help="gait candidates per state (1: every instance its own state, no duplicate QPs)")
 ap.add_argument("--rounds", type=int, default=8)
 ap.add_argument("--per", type=int, default=16)
 ap.add_argument("--slot", type=int, default=2,
@@ -28,7 +30,7 @@ from mpcqp.engine import BatchEngine  # noqa: E402
 
 p = mpcqp.model_params(args.config)
 for B in [int(b) for b in args.batches.split(",")]:
-    batch = mpcqp.make_batch(p, B, gait=args.gait)
+    batch = mpcqp.make_batch(p, B, candidates=args.candidates, gait=args.gait)
     engs = []
     for spec in args.env:
         k, v = spec.split("=", 1)
@@ -52,7 +54,7 @@ for B in [int(b) for b in args.batches.split(",")]:
             e.sync()
             ms, n = e.kernel_ms_sum(args.slot)
             res[spec].append(ms / max(1, n))
-    line = [f"{args.config}@{B} ({args.gait})"]
+    line = [f"{args.config}@{B} ({args.gait}, {args.candidates} candidates)"]
     for spec, e, d in engs:
         it = d["iters"].cpu().numpy()
         r = np.array(res[spec])

@@ -93,5 +93,16 @@ case "$NAME" in
   pair-sort)   log rep 3 ab_b nosort ;;                 # schedule-sorted pairing off (nosort: -DMPCQP_PAIR_SORT=0)
   toep-pipe)   log rep 3 ab_e default toeppipe_e ;;     # E: software-pipelined Toeplitz tiles (NOILP=1 TU=fast_dense toeppipe_e:-DMPCQP_TOEP_PIPE=1)
   wg-crash-k)  log rep 3 ab_e default kc24_e kc16_e ;;   # E: workgroup crash KC (NOILP=1 TU=fast_dense kc24_e:-DMPCQP_WG_CRASH_K=24 ...)
+  pair-dedup)  # duplicate QPs of a group solved once: same-binary A/B (MPCQP_PAIR_DEDUP 0 / default) on the
+               # benchmark batch, on a batch without duplicates (1 candidate per state: the price of the
+               # ranking and of the member checks) and on one state repeated (every wave but one covered)
+    dd() { timeout -k 10 300 python3 tools/ab_env.py --env MPCQP_PAIR_DEDUP=0 --env MPCQP_PAIR_DEDUP= "$@"; }
+    log eval 'dd --batches 2048,4096,8192,16384,65536 && dd --batches 65536 --candidates 1 &&
+              dd --batches 65536 --candidates 65536 && dd --batches 65520 && dd --batches 65520 --candidates 1' ;;
+  pair-dedup-parent)  # the same control against the parent's library (lib/libmpcqp_parent.so), back to back;
+                      # then 65,520 instances (4,095 whole groups: a group's wavefronts spread over the XCDs)
+    log eval 'rep 3 abl "AB_CONFIGS=B AB_REPS=60 AB_CANDS=1 AB_B2B=1" default parent &&
+              rep 2 abl "AB_CONFIGS=B AB_REPS=60 AB_CANDS=1 AB_B2B=1 AB_BATCH=65520" default parent &&
+              rep 2 abl "AB_CONFIGS=B AB_REPS=60 AB_B2B=1 AB_BATCH=65520" default parent' ;;
   *) echo "unknown run: $NAME" >&2; exit 2 ;;
 esac

@@ -14,6 +14,8 @@ ap.add_argument("--batch", type=int, default=65536)
 ap.add_argument("--reps", type=int, default=20)
 ap.add_argument("--gait", default="alternating")
 ap.add_argument("--max-free", type=int, default=None)
+ap.add_argument("--candidates", type=int, default=16,
+                help="gait candidates per state (1: no duplicate QPs in the batch)")
 ap.add_argument("--b2b", action="store_true",
                 help="launches back to back (no sync between them, as bench.py's steps), the "
                      "one-wave kernel's mean by the library's events (slot 2) after 50 warm-up calls")
@@ -26,7 +28,7 @@ for cfg in args.configs.split(","):
     if args.max_free is not None:
         p["max_free"] = args.max_free
     eng = BatchEngine(p)
-    d = eng.upload(mpcqp.make_batch(p, args.batch, gait=args.gait))
+    d = eng.upload(mpcqp.make_batch(p, args.batch, candidates=args.candidates, gait=args.gait))
     if args.b2b:
         for _ in range(50):
             eng.solve(d)
